@@ -23,7 +23,13 @@ collectives, the device work between them replayed from hipGraphs.  --shard rows
 rows-within-list shards (every rank searches every query; A/B only).  Per-GPU queries are fixed
 as N grows ("weak").
 
-Besides the QPS line the JSON carries:
+A plain run sets up, warms up, times --steps steps and prints the QPS line (metric, value, unit,
+ms_per_step, the configuration).  --dump-outputs DIR also writes what the last timed step returned
+(DIR/scores.npy, DIR/labels.npy; the inputs are seeded, so two builds compare output for output).
+
+With --full the run goes on after the timed steps and the JSON also carries:
+  graph_check   the last replay's answer against a kernel-by-kernel search of the same batch
+  phases_ms     per-phase kernel times (HIP events), over --profile-steps further steps
   roofline      the dominant kernel (IVF list scan) timed with HIP events on its own stream:
                 unique algorithmic bytes (every probed list once + queries) per launch against
                 the HBM peak; "mfma" gives the as-executed MFMA rate
@@ -81,7 +87,32 @@ def parse(argv=None):
     ap.add_argument("--graph", type=int, default=1,
                     help="N = 1: replay each step from a HIP graph of the whole search (1, default) or launch it "
                          "kernel by kernel (0); every replay runs every kernel of the search")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the graph check, the per-phase profile, the roofline, "
+                         "recall@10 and the CPU baseline (--profile-steps, --recall-queries, --cpu-seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's answer to DIR/scores.npy (float32) and DIR/labels.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs writes less than 64 MB in all
+
+
+def dump_outputs(path, scores, labels):
+    """--dump-outputs: the answer of the last timed step as a caller receives it, scores as float32 and labels
+    as float64 (row ids, exact below 2^53).  Past DUMP_BYTES a fixed, seeded sample of the queries is kept and
+    their positions in the batch go to rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    per_query = scores.shape[1] * (4 + 8) + 8
+    if len(scores) * per_query > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(scores), DUMP_BYTES // per_query, replace=False))
+        scores, labels = scores[rows], labels[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), np.ascontiguousarray(scores, dtype=np.float32))
+    np.save(os.path.join(path, "labels.npy"), labels.astype(np.float64))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -225,7 +256,7 @@ def run(args):
     t = time.time()
     idx = IvfFlatVectorIndex(D, VectorMetric.L2, n_list=args.nlist, device=local)
     idx.set_centroids(cents)
-    keep = world == 1 and args.cpu_seconds > 0  # the CPU baseline reads base rows
+    keep = args.full and world == 1 and args.cpu_seconds > 0  # the CPU baseline reads base rows
     kept = []
     nrows = 0
     lists_sharded = world > 1 and args.shard == "lists"
@@ -354,6 +385,63 @@ def run(args):
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # list-sharded: rank 0 holds the answers of its home queries
+        o_s, o_l = (s_loc, l_loc) if world == 1 else (result[0], result[1])
+        dump_outputs(args.dump_outputs, o_s.cpu().numpy(), o_l.cpu().numpy())
+    if world > 1:
+        e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(e, op=dist.ReduceOp.MAX)
+        elapsed = float(e.item())
+    qps = Q * args.steps / elapsed
+    log(f"rank {rank}: {args.steps} steps in {elapsed * 1e3:.1f} ms -> {qps:,.0f} QPS")
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "QPS + recall@10, IVF-Flat d=128 N=10M nprobe=32 at 1/2/4/8 MI355X",
+            "value": qps,
+            "unit": "queries/s",
+            "n_gpus": world,
+            "ranks_seen": dist.get_world_size() if world > 1 else 1,
+            "backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else " (rehearsal: one GPU)"))
+                       if world > 1 else None,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",  # results and the certified refine are fp32; the filter streams fp16 tiles
+            "data": "synthetic: Pyrope.Benchmarks generator (.NET Random), base rows in 65,536-row blocks seeded "
+                    "42 + block, queries seed 1337, uniform [0,1)",
+            "config": {"workload": f"IVF_FLAT d={D} N={N} nlist={args.nlist} nprobe={args.nprobe} k={k}",
+                       "n": N, "dim": D, "nlist": args.nlist, "nprobe": args.nprobe, "k": k,
+                       "queries_per_step": Q, "queries_per_gpu": args.nq, "train_rows": T,
+                       "shard": ("whole IVF lists per rank (size-balanced), rows exchanged to their list's owner, "
+                                 "replicated list samples; shared quantizer (trained on rank 0, broadcast)"
+                                 if lists_sharded else
+                                 "rows-within-list: generator blocks b % n_gpus == rank, shared quantizer "
+                                 "(trained on rank 0, broadcast)") if world > 1 else "none",
+                       "merge": ("RCCL all_gather of plans, all_to_all of per-query records to their home rank, "
+                                 "on-device merge + certificate, exact re-run of failures (all_gather + all_to_all)"
+                                 if lists_sharded else
+                                 "RCCL all_gather of probe lists and of partial top-k + on-device merge")
+                                if world > 1 else "none"},
+            "launch": "hipGraph replay of the whole search per step" if graph is not None else "kernel launches",
+            "full": args.full,
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        idx.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run ends here
+        finish()
+        return
+
     # the timed replays' answer (the last replay's results) against a plain kernel-by-kernel search of the same
     # batch: bit-identical, so the graph replays computed the search (DESIGN.md §4 "hipGraph replays")
     graph_check = None
@@ -373,12 +461,6 @@ def run(args):
                        "last_replay_equals_direct_search": bool(torch.equal(g_l, o_l)) and
                        bool(torch.equal(g_s.view(torch.int32), o_s.view(torch.int32)))}
         log(f"graph replay vs direct search: {graph_check}")
-    if world > 1:
-        e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(e, op=dist.ReduceOp.MAX)
-        elapsed = float(e.item())
-    qps = Q * args.steps / elapsed
-    log(f"rank {rank}: {args.steps} steps in {elapsed * 1e3:.1f} ms -> {qps:,.0f} QPS")
 
     # ---- per-phase kernel times (HIP events on the search stream), outside the timed region ----
     phases = {}
@@ -566,36 +648,7 @@ def run(args):
                               "home's count); failures past fcap are re-run in further rounds"}
     if rank == 0:
         bytes_per_query = args.nprobe / args.nlist * N * D * 4 + args.nlist * D * 4
-        out = {
-            "metric": "QPS + recall@10, IVF-Flat d=128 N=10M nprobe=32 at 1/2/4/8 MI355X",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else " (rehearsal: one GPU)"))
-                       if world > 1 else None,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",  # results and the certified refine are fp32; the filter streams fp16 tiles
-            "data": "synthetic: Pyrope.Benchmarks generator (.NET Random), base rows in 65,536-row blocks seeded "
-                    "42 + block, queries seed 1337, uniform [0,1)",
-            "config": {"workload": f"IVF_FLAT d={D} N={N} nlist={args.nlist} nprobe={args.nprobe} k={k}",
-                       "n": N, "dim": D, "nlist": args.nlist, "nprobe": args.nprobe, "k": k,
-                       "queries_per_step": Q, "queries_per_gpu": args.nq, "train_rows": T,
-                       "shard": ("whole IVF lists per rank (size-balanced), rows exchanged to their list's owner, "
-                                 "replicated list samples; shared quantizer (trained on rank 0, broadcast)"
-                                 if lists_sharded else
-                                 "rows-within-list: generator blocks b % n_gpus == rank, shared quantizer "
-                                 "(trained on rank 0, broadcast)") if world > 1 else "none",
-                       "merge": ("RCCL all_gather of plans, all_to_all of per-query records to their home rank, "
-                                 "on-device merge + certificate, exact re-run of failures (all_gather + all_to_all)"
-                                 if lists_sharded else
-                                 "RCCL all_gather of probe lists and of partial top-k + on-device merge")
-                                if world > 1 else "none"},
+        out.update({
             "recall_at_10": recall,
             "recall_truth_check": truth_check,
             "roofline": {"bound": "hbm", "achieved": hbm_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -624,7 +677,6 @@ def run(args):
             "per_query_bytes": {"bytes_per_query": bytes_per_query,
                                 "note": "SURVEY.md 8(d): nprobe/nlist x N x D x 4 + nlist x D x 4 per query (no "
                                         "batching reuse); not a roofline"},
-            "launch": "hipGraph replay of the whole search per step" if graph is not None else "kernel launches",
             "graph_check": graph_check,
             "phases_ms": {k_: round(v["ms"], 4) for k_, v in phases.items()},
             "collective_ms": {k_: round(v, 4) for k_, v in coll.items()} if world > 1 else None,
@@ -633,12 +685,8 @@ def run(args):
             "shard_messages": shard_messages,
             "shard_certificate": shard_cert,
             "cpu_baseline": cpu,
-        }
-        print(json.dumps(out), flush=True)
-    idx.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+        })
+    finish()
 
 
 def main():

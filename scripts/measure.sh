@@ -5,7 +5,7 @@
 #
 # Steps (each under its own time limit; the exit status is the step's, so steps chain with &&):
 #   tests <secs> [pytest args...]      the -m gpu suite (or the given test paths), verbose, per-test timeout
-#   bench <name> <secs> [bench args]   python bench.py ... -> <outdir>/<name>.log; prints the JSON's headline
+#   bench <name> <secs> [bench args]   python bench.py --full ... -> <outdir>/<name>.log; prints the JSON's headline
 #   kt <name> <secs> [bench args]      the same under rocprofv3 --kernel-trace --stats (csv under <outdir>/<name>/)
 #   pmc <name> <counters> [bench args] one rocprofv3 --pmc pass (its own run; counters of one block budget)
 #   aux <name> <secs> <script> [args]  python -u <script> args -> <outdir>/<name>.log
@@ -47,14 +47,14 @@ case "$step" in
     exit $rc ;;
   bench)
     name=$1; secs=$2; shift 2
-    timeout -k 10 "$secs" python -u bench.py "$@" > "$O/$name.log" 2>&1
+    timeout -k 10 "$secs" python -u bench.py --full "$@" > "$O/$name.log" 2>&1
     rc=$?
     [ $rc -ne 0 ] && { tail -n 30 "$O/$name.log"; exit $rc; }
     echo "$name: $(headline "$O/$name.log")" ;;
   kt)
     name=$1; secs=$2; shift 2
     timeout -k 10 "$secs" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$name" -o run -- \
-      python3 bench.py "$@" > "$O/$name.log" 2>&1
+      python3 bench.py --full "$@" > "$O/$name.log" 2>&1
     rc=$?
     [ $rc -ne 0 ] && { tail -n 30 "$O/$name.log"; exit $rc; }
     echo "$name: $(headline "$O/$name.log")" ;;

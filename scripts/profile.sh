@@ -15,7 +15,7 @@ P=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$P"
 cd "$ROOT" || exit 1
 REGEX=${PYR_PROF_REGEX:-scan_|mfma_filter}
-B="--cpu-seconds 0 --recall-queries 0"
+B="--full --cpu-seconds 0 --recall-queries 0"
 
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format rocpd csv -d "$P/kt" -o run -- \
   python bench.py --steps 10 --warmup 2 $B "$@" > "$P/kt_bench.json" 2> "$P/kt_bench.log" || exit $?
