@@ -727,8 +727,20 @@ static bool filter_enabled() {
   const char *e = knob("PYR_FILTER");
   return !(e && atoi(e) == 0);
 }
-// fp16 tiles are kept where the stream scan can use them (L2 / IP, tile dims up to 768)
+// fp16 tiles are kept where the stream scan can use them (L2 / IP, tile dims up to 2048)
 static bool store16(int dim, int metric) { return (metric == L2 || metric == IP) && scan_tile_dim(dim) > 0; }
+// Tile dims >= 1024 (32 or 64 queries per item: every item of a list chunk re-reads its 64 - 128 KiB tiles): the
+// items in XCD order, so that one chunk's items run on one XCD and its L2 serves the re-reads (scan.hip XQ, as
+// pq32.hip); PYR_SCAN_XCD=0: list order, one queue (A/B; same results)
+static int scan_xcd(int dt) {
+  if (!scan_item_queues(dt)) return 0;
+  const char *e = knob("PYR_SCAN_XCD");
+  return e && atoi(e) == 0 ? 0 : 1;
+}
+// the main scan's item counters in ws.swork (zeroed with the slice's counters): one word, or the second set of 8
+static int32_t *scan_main_work(Workspace &ws, int dt) {
+  return ws.swork.as<int32_t>() + (scan_item_queues(dt) ? 8 : 1);
+}
 // the tile dimension of a store of dim (zero-padded for the stream scan)
 static int store16_dt(int dim) { return scan_tile_dim(dim); }
 // the query operands and the sample of the stream scan: at tile dim = dim = 32 / 64 / 128 sprep + the
@@ -1397,7 +1409,8 @@ struct FlatIndex : Index {
   // path's lists (every query probes all of them, their centroid the store's center: mu for L2, 0 for IP),
   // so the sample, the emit scan, the merge and the certified refine (the *Unsafe form, V = 4) run as
   // for IVF_FLAT, and the exact re-run of certificate failures stays on the device: no host round trip.
-  // Anything else (k > 60, dims past 768, an L2 store without its centre) takes the exact scan.
+  // Anything else (dims past 2048, an L2 store without its centre, a topK past the deep refine's) takes the
+  // exact scan.
   bool flat_stream_ok(int k, int k1, int64_t cutoff) const {
     if (!filter_enabled()) return false;
     if (metric != L2 && metric != IP) return false;
@@ -1470,7 +1483,7 @@ struct FlatIndex : Index {
   void stream_slice(const float *d_q, int64_t nq, int k, int k1, int64_t cutoff, int nch, int nparts, int cap,
                     float *d_s, int64_t *d_l, int32_t *d_c, Workspace &ws, const CosRefine *cr = nullptr) {
     const int probes = nch;
-    const IvfChunking ch{(int32_t)flat_chunk_rows(cutoff), 1, 0};
+    const IvfChunking ch{(int32_t)flat_chunk_rows(cutoff), 1, 0, 0, scan_xcd(st.tdim())};
     reset_stream_counters(ws, nq, nch);
     ws.probes.ensure(sizeof(int32_t) * nq * probes);
     launch_iota_rows(ws.probes.as<int32_t>(), nq, probes, ws.st);
@@ -1542,7 +1555,7 @@ struct FlatIndex : Index {
       sel.thr = ws.sthr.as<float>();
       launch_stream_select(sel, ws.st);
     }
-    sa.work = ws.swork.as<int32_t>() + 1;
+    sa.work = scan_main_work(ws, dt);
     {
       PhaseTimer t(PH_FLAT_SCAN, ws.st, nq * cutoff);
       launch_scan_main(main_scan_args(sa), metric, maxi, ws.st);
@@ -2468,7 +2481,8 @@ struct IvfFlatIndex : Index {
   }
 
   // the lists' fp16 residual tiles serve this search's stream scan (scan.hip) at every tile dimension;
-  // anything else (k > 60, MaxScans, dims past 768, an unbuilt index) takes the exact scan
+  // (up to 2048); anything else (dims past 2048, an unbuilt index, a topK past the deep refine's) takes the
+  // exact scan
   bool stream_ok(int k1) const {
     if (!lists.f16 || !lists.resid) return false;
     const int met = metric == COS ? L2 : metric;
@@ -2487,7 +2501,7 @@ struct IvfFlatIndex : Index {
     int64_t chunk = stream_chunk();
     // a list-sharded rank's lists it does not own are empty: their (query, list) pairs get no item.  Not
     // otherwise: the sample pass writes the (empty) sample of an empty list's pairs through its item
-    IvfChunking ch{(int32_t)chunk, 1, 0, sh ? 1 : 0};
+    IvfChunking ch{(int32_t)chunk, 1, 0, sh ? 1 : 0, scan_xcd(lists.tdim())};
     ch.cmax = std::max(1, ivf_list_chunks((int)max_len, ch));
     if ((int64_t)probes * ch.cmax > MAX_PARTS) {  // fewer, longer chunks
       const int64_t room = std::max<int64_t>(1, MAX_PARTS / std::max(probes, 1));
@@ -2685,7 +2699,7 @@ struct IvfFlatIndex : Index {
         launch_stream_select(sel, ws.st);
       }
     }
-    sa.work = ws.swork.as<int32_t>() + 1;
+    sa.work = scan_main_work(ws, dt);
     {
       PhaseTimer t(PH_LIST_SCAN, ws.st, prof().on && !sh ? probed_rows(ws, nq, probes, le, lb) : 0);
       if (timing) sa.tdbg = ws.tdbg.as<unsigned long long>();

@@ -531,10 +531,14 @@ int device_cus();                   // compute units of the current device (pers
 // the 32x32x16 list scan; sample16.hip: sprep + the 8-wave sample of tile dims 32 / 64 / 128 (same
 // outputs: bq, qsc, samp with scan_sample_values() values per (query, probe))
 int scan_sample_values();
-// tile dimension of the stream scan for a row dimension: dims <= 128 rounded up to 32, then 256 / 512 / 768
-// (tiles and query operands zero-padded; the fp32 rows and the exact refine keep dim); 0 = none
+// tile dimension of the stream scan for a row dimension: dims <= 128 rounded up to 32, then 256 / 512 / 768 /
+// 1024 / 1536 / 2048 (tiles and query operands zero-padded; the fp32 rows and the exact refine keep dim);
+// 0 = none (dims past 2048: the exact scan)
 int scan_tile_dim(int dim);
 int scan_qmax(int dt);               // queries per work item at tile dimension dt
+// tile dims >= 1024: launch_scan_main takes its items from the 8 queues bounded by n_items[1 .. 9] (written by
+// every build_ivf_items; IvfChunking::xcd puts a list's items on one XCD) with work[0 .. 7] as their counters
+bool scan_item_queues(int dt);
 bool scan_supported(int dim, int metric, int k1);
 // FLAT chunks as lists: lb/le of nch chunks of crow rows over [0, cutoff), each with the centroid center
 // (null: 0) -> cents [nch][dim]

@@ -43,14 +43,25 @@ namespace {
 constexpr int SAMPLE_TILES = 16;       // tiles of a list the sample scores (stream16.hip: 2 x 8 waves)
 constexpr int SV = 2 * SAMPLE_TILES;   // sample values per (query, probe): one per (tile, lane half)
 
-// Tile dimensions (scan_tile_dim): dims up to 128 rounded up to 32; 256, 512, 768.  Per tile dimension
-// the queries per item (the item's fp16 query operands fill <= 128 KB of LDS) and the waves per block
-// (16 while a tile's A operands and a group's B operands fit 128 VGPRs, else 8).
+// Tile dimensions (scan_tile_dim): dims up to 128 rounded up to 32; 256, 512, 768, 1024, 1536, 2048.  Per
+// tile dimension the queries per item (the item's fp16 query operands fill <= 128 KB of LDS: 64 queries up
+// to 1024, one 32-query group above) and the waves per block (16 while a tile's A operands and a group's B
+// operands fit 128 VGPRs, else 8).  Past 2048 a single group's operands no longer fit the LDS (3072: 192 KB):
+// 0, the exact scan.
 constexpr int tile_dim_of(int dim) {
-  return dim <= 0 ? 0 : dim <= 128 ? (dim + 31) / 32 * 32 : dim <= 256 ? 256 : dim <= 512 ? 512 : dim <= 768 ? 768 : 0;
+  return dim <= 0      ? 0
+         : dim <= 128  ? (dim + 31) / 32 * 32
+         : dim <= 256  ? 256
+         : dim <= 512  ? 512
+         : dim <= 768  ? 768
+         : dim <= 1024 ? 1024
+         : dim <= 1536 ? 1536
+         : dim <= 2048 ? 2048
+                       : 0;
 }
-constexpr int qmax_of(int D) { return D <= 128 ? 512 : D == 256 ? 256 : D == 512 ? 128 : 64; }
+constexpr int qmax_of(int D) { return D <= 128 ? 512 : D == 256 ? 256 : D == 512 ? 128 : D <= 1024 ? 64 : 32; }
 constexpr int nw_of(int D) { return D <= 128 ? 16 : 8; }
+constexpr bool xq_of(int D) { return D >= 1024; }  // the main scan's items come from per-XCD queues
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(a, fmaxf(b, c)); }
 
@@ -264,7 +275,9 @@ __global__ __launch_bounds__(64 * nw_of(D), 1) void scan_kernel(StreamArgs a) {
   constexpr int QMAX = qmax_of(D);   // queries per item
   constexpr int NG = QMAX / 32;      // query groups per item
   constexpr int PIECES = NG * KS;
-  static_assert(KS % KC == 0 && QMAX <= 512, "tile dimension");
+  // (QMAX <= 512: a query slot fits the staged word's 9 bits above the 23-bit row offset; the operands leave
+  // the staging at least 3,840 entries -- D = 1024 -- 480 per wave at 8 waves)
+  static_assert(KS % KC == 0 && QMAX <= 512 && QMAX % 32 == 0 && PIECES * 1024 <= 131072, "tile dimension");
   __shared__ __attribute__((aligned(16))) char bl[PIECES * 1024];
   __shared__ float2 qf[QMAX];        // per query slot: {f, threshold in y = f acc + row term space}
   __shared__ float2 qz[QMAX];        // {cq (score = y + cq), the query as int bits}
@@ -306,12 +319,30 @@ __global__ __launch_bounds__(64 * nw_of(D), 1) void scan_kernel(StreamArgs a) {
   // tiles, so the round trips sit inside the end-of-item barrier instead of before each prologue (round 6).
   // The sample pass (a.lioff) takes LISTS from its counter and walks each list's chunk-0 items
   // (lioff[l] .. + ceil(lcnt[l] / lqchunk)), instead of drawing and skipping the other chunks' items.
+  // XQ (tile dims >= 1024): items from 8 per-XCD queues, as pq32.hip's pq_next_item (n_items[1 .. 9]: the queues'
+  // item bounds, work[0 .. 7]: their counters; blocks b and b + 8 share an XCD).  With the items in XCD order
+  // (IvfChunking::xcd) the items of one list chunk -- ten of them at 32 queries per item -- run on one XCD, whose L2
+  // then serves their re-reads of the chunk's tiles; in list order the builder leaves one queue holding every item.
+  constexpr bool XQ = xq_of(D);
   const int nit = *a.n_items;
   int sm_l = 0, sm_g = 0, sm_ng = 0;  // (thread 0: the sample pass's current list)
+  int xq_q = blockIdx.x & 7, xq_tried = 0;  // (thread 0: the block's current queue, queues found empty)
   int par = 0;  // (block-uniform) the current item's slot
   auto fetch = [&](int slot) {
     int nx;
-    if (SMP && a.lioff) {
+    if constexpr (XQ) {
+      const int32_t *qb = a.n_items + 1;
+      nx = nit;
+      while (xq_tried < 8) {
+        const int t = atomicAdd(a.work + xq_q, 1);
+        if (qb[xq_q] + t < qb[xq_q + 1]) {
+          nx = qb[xq_q] + t;
+          break;
+        }
+        xq_q = (xq_q + 1) & 7;
+        ++xq_tried;
+      }
+    } else if (SMP && a.lioff) {
       if (sm_g < sm_ng) {
         nx = a.lioff[sm_l] + sm_g++;
       } else {
@@ -737,6 +768,9 @@ void launch_sample_dm(const StreamArgs &a, int max_items, hipStream_t st) {
     case 256: return metric == L2 ? fn<256, L2>(a, max_items, st) : fn<256, IP>(a, max_items, st); \
     case 512: return metric == L2 ? fn<512, L2>(a, max_items, st) : fn<512, IP>(a, max_items, st); \
     case 768: return metric == L2 ? fn<768, L2>(a, max_items, st) : fn<768, IP>(a, max_items, st); \
+    case 1024: return metric == L2 ? fn<1024, L2>(a, max_items, st) : fn<1024, IP>(a, max_items, st); \
+    case 1536: return metric == L2 ? fn<1536, L2>(a, max_items, st) : fn<1536, IP>(a, max_items, st); \
+    case 2048: return metric == L2 ? fn<2048, L2>(a, max_items, st) : fn<2048, IP>(a, max_items, st); \
     default: throw_unsupported(dt);                                                         \
   }
 
@@ -777,6 +811,7 @@ void launch_iota_rows(int32_t *out, int64_t rows, int cols, hipStream_t st) {
 int scan_sample_values() { return SV; }
 int scan_tile_dim(int dim) { return tile_dim_of(dim); }
 int scan_qmax(int dt) { return qmax_of(dt); }
+bool scan_item_queues(int dt) { return xq_of(dt); }
 bool scan_supported(int dim, int metric, int k1) {
   return (metric == L2 || metric == IP) && tile_dim_of(dim) > 0 && k1 >= 1 && k1 <= 512;  // (> 64: deep refine)
 }
