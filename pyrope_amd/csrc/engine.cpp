@@ -2258,7 +2258,10 @@ struct IvfFlatIndex : Index {
                     const float *C, int k) {
     // stable list-major layout, lists padded to 8 rows
     std::vector<int32_t> cnt(k, 0);
-    for (int32_t a : asg) cnt[a]++;
+    for (int32_t a : asg) {
+      if (a < 0 || a >= k) throw Error(PYR_E_STATE, "a row's list is outside the quantizer");
+      cnt[a]++;
+    }
     lb.assign(k, 0);
     le.assign(k, 0);
     llen = cnt;
@@ -2813,7 +2816,9 @@ struct IvfFlatIndex : Index {
     }
     if (sh) {  // list-sharded: the records (exact local top-k + bound); the home rank's merge certifies
       PhaseTimer t(PH_REFINE, ws.st, nq * k1);
-      r.k1 = k1;
+      // the fused kernel goes on to depth 64 where the rank's own depth-K1 certificate fails, as the unsharded
+      // search does; the two-launch form (PYR_MERGE_REFINE=0, A/B) refines every record at depth 64
+      r.k1 = fused ? k1 : STREAM_KO;
       r.rec = sh->rec;
       r.rec_lb = dlb.as<int32_t>();
       r.rec_nlist = coarse.nlist;
@@ -3027,8 +3032,11 @@ struct IvfFlatIndex : Index {
     auto f = pos_of.find(label);
     return f == pos_of.end() ? -1 : f->second;
   }
+  bool ms_dealable() const override {
+    return built && coarse.nlist > 0 && metric != COS && stream_ok(filter_k1(1));
+  }
   bool ms_shardable(int k, const pyr_search_params &prm, int *P) const override {
-    if (!built || coarse.nlist <= 0 || metric == COS || buf.live_count() > 0 || !filter_enabled()) return false;
+    if (!ms_dealable() || buf.live_count() > 0 || !filter_enabled()) return false;
     const int k1 = filter_k1(k);
     if (k <= 0 || k > KMAX_FAST || k1 <= 0 || !stream_ok(k1)) return false;
     const int nprobe = prm.nprobe < 0 ? nprobe_default : prm.nprobe;

@@ -353,6 +353,9 @@ struct Index {
     (void)label;
     return -1;
   }
+  // the lists can be dealt to shards (built, L2 / IP, fp16 residual tiles the stream scan reads): a property of
+  // the built lists alone -- rows waiting in the buffer do not keep the lists from being dealt
+  virtual bool ms_dealable() const { return false; }
   // the list-sharded step answers this search (built, empty buffer, L2 / IP, k within the stream scan's refine);
   // else the stage searches alone; *P = the probe width
   virtual bool ms_shardable(int k, const pyr_search_params &p, int *P) const {

@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void refine_kernel(RefineArgs a) {
 // placeholder max(T_q, floor)); the candidates of depth K1 are re-scored exactly and certified as in
 // refine_kernel's upper-bound branch; a query that fails goes on to depth 64 in the same wave (its other 48
 // candidates scored then), and what fails there is listed for the exact re-run.  Shard records (a.rec): the
-// depth-K1 answer and bound, no certificate.
+// answer and bound of the depth the rank's own certificate stops at (K1, else 64); the home's merge certifies.
 template <int V, int MET, int DT>
 __global__ __launch_bounds__(256) void merge_refine_kernel(CandMergeArgs m, RefineArgs a) {
   const int lane = threadIdx.x & 63;
@@ -504,7 +504,29 @@ __global__ __launch_bounds__(256) void merge_refine_kernel(CandMergeArgs m, Refi
   };
   score_passes(0, k1 / 8);
   rank_at(k1);
-  if (a.rec) {  // list-sharded record (see refine_kernel)
+  const double u = 5.9604644775390625e-8;  // 2^-24
+  auto certified = [&]() -> bool {
+    if (!excluded) return true;  // no row was left out
+    if (MET == L2 && a.cosine) {
+      const float qn = a.qnorm[q];
+      return nout == k && (double)skth > 1.0 + 0.5 * (double)bound + (2.0 * D + 256.0) * u && qn >= 1e-6f &&
+             isfinite(qn) && !(a.max_rsq && a.max_rsq[1] != 0u) && !(a.zflag && *a.zflag != 0u && !(skth > 0.0f));
+    }
+    return nout == k && skth > bound;
+  };
+  bool ok = certified();
+  if (!ok && d < STREAM_KO && k + 4 <= STREAM_KO) {  // (wave-uniform) the same candidates at depth 64
+    score_passes(k1 / 8, STREAM_KO / 8);
+    d = STREAM_KO;
+    rank_at(d);
+    ok = certified();
+  }
+  if (a.rec) {
+    // list-sharded record (see refine_kernel): this rank's exact top-k of depth d's candidates and the bound of
+    // everything past depth d.  The depth is chosen as the unsharded search chooses it: a rank whose own k-th
+    // score beats its depth-K1 bound stops there (the merged k-th score is no lower than any rank's, so the home's
+    // certificate holds against that bound too); any other rank -- one that holds fewer than k of the query's
+    // candidates included -- reports the depth-64 bound, the one the unsharded search would certify against
     uint8_t *rp = static_cast<uint8_t *>(a.rec) + (size_t)q * shard_record_bytes(k);
     ShardEntry *ent = reinterpret_cast<ShardEntry *>(rp);
     if (key != KEY_NONE && rank < k) {
@@ -529,23 +551,6 @@ __global__ __launch_bounds__(256) void merge_refine_kernel(CandMergeArgs m, Refi
       *reinterpret_cast<ShardTrailer *>(rp + 16 * (size_t)k) = t;
     }
     return;
-  }
-  const double u = 5.9604644775390625e-8;  // 2^-24
-  auto certified = [&]() -> bool {
-    if (!excluded) return true;  // no row was left out
-    if (MET == L2 && a.cosine) {
-      const float qn = a.qnorm[q];
-      return nout == k && (double)skth > 1.0 + 0.5 * (double)bound + (2.0 * D + 256.0) * u && qn >= 1e-6f &&
-             isfinite(qn) && !(a.max_rsq && a.max_rsq[1] != 0u) && !(a.zflag && *a.zflag != 0u && !(skth > 0.0f));
-    }
-    return nout == k && skth > bound;
-  };
-  bool ok = certified();
-  if (!ok && d < STREAM_KO && k + 4 <= STREAM_KO) {  // (wave-uniform) the same candidates at depth 64
-    score_passes(k1 / 8, STREAM_KO / 8);
-    d = STREAM_KO;
-    rank_at(d);
-    ok = certified();
   }
   if (key != KEY_NONE && rank < k) {
     a.out_s[(size_t)q * k + rank] = s;

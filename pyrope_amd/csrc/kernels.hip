@@ -1407,7 +1407,11 @@ __global__ void gather_rows_kernel(const T *src, const int32_t *idx, int64_t n, 
 // ---------------------------------------------------------------------------
 __global__ void keys_to_assign_kernel(const uint32_t *keys, int64_t n, int32_t *assign) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) assign[i] = (int32_t)keys[i];
+  // a row whose scores are all NaN leaves the top-1 scan without a key: FindNearestCentroid's bestIndex stays 0
+  // (KMeansUtils.cs:72-92, no score > float.MinValue).  Every assign_gpu caller gets this: Build's assignment and
+  // k-means training, where such a row joins cluster 0 (whose NaN mean ArraysEqual then takes for unchanged, :57,
+  // :95-101: the centroid stays as it was), as in the reference
+  if (i < n) assign[i] = keys[i] == KEY_NONE ? 0 : (int32_t)keys[i];
 }
 
 // one thread per (cluster, dim): members summed in data order, then / Count.

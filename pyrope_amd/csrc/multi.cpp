@@ -239,16 +239,15 @@ struct MultiIvfIndex : Index {
         fail_round, rrec, rrec_home;
   };
   std::vector<std::unique_ptr<Rank>> rk;
-  int64_t last_max_fail = 0, last_rounds = 0;
-  std::atomic<int64_t> n_sharded{0}, n_staged{0};
+  std::atomic<int64_t> last_max_fail{0}, last_rounds{0}, n_sharded{0}, n_staged{0};
   void shard_info(int32_t *shards, int32_t *xport, int64_t *sharded, int64_t *staged, int64_t *max_fail,
                   int64_t *rounds) const override {
     *shards = W;
     *xport = !xp ? 0 : std::strcmp(xp->name(), "RCCL") == 0 ? 2 : 1;
     *sharded = n_sharded.load();
     *staged = n_staged.load();
-    *max_fail = last_max_fail;
-    *rounds = last_rounds;
+    *max_fail = last_max_fail.load();
+    *rounds = last_rounds.load();
   }
 
   explicit MultiIvfIndex(const pyr_index_desc &d) : Index(d) {
@@ -383,9 +382,10 @@ struct MultiIvfIndex : Index {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(stage->wst));
     if (!stage->ms_lists(L)) return;
-    int P0 = 0;
-    const pyr_search_params p0{-1, 0, -1};
-    if (!stage->ms_shardable(1, p0, &P0)) return;  // Cosine, dims without fp16 tiles: the stage answers alone
+    // Cosine, dims without fp16 tiles: the stage answers alone.  A non-empty buffer (a loaded image's rows written
+    // after its Build) does not stop the deal: only visible list rows are dealt, and search() keeps sending every
+    // search to the stage until the buffer is empty again
+    if (!stage->ms_dealable()) return;
     const int nl = L.nlist;
     owner = list_owners(L.llive, W);
     // every shard's visible rows in list order (labels: their stage positions), and each list's first rows

@@ -183,6 +183,9 @@ __global__ __launch_bounds__(256) void sample_kernel(StreamArgs a) {
   const int r0 = it.row_begin;
   const int nt = min((it.row_end - r0 + 31) >> 5, SAMPLE_TILES);
   const char *hsrc = reinterpret_cast<const char *>(a.h16);
+  // MaxScans (a.plim): only the rows before the pair's bound are sampled, as scan_kernel's SMP + LIM form does at
+  // the native dims -- T_q from rows the scan will not reach leaves too few candidates for the certificate
+  const uint32_t lim = a.plim ? min(a.plim[pos], (uint32_t)it.row_end) : (uint32_t)it.row_end;
   float mx[SAMPLE_TILES];
 #pragma unroll
   for (int t = 0; t < SAMPLE_TILES; ++t) {
@@ -206,14 +209,14 @@ __global__ __launch_bounds__(256) void sample_kernel(StreamArgs a) {
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v *>(tb + s * 1024), operand(s), acc,
                                                        0, 0, 0);
       }
-      const int rt = r0 + 32 * t, rlim = it.row_end;
+      const int rt = r0 + 32 * t;
       float m = -INFINITY;
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float y = fmaf(f, acc[4 * b + i], M[b][i]);
-          m = rt + 8 * b + 4 * h + i < rlim ? fmaxf(m, y) : m;
+          m = (uint32_t)(rt + 8 * b + 4 * h + i) < lim ? fmaxf(m, y) : m;
         }
       mx[t] = m;
     }

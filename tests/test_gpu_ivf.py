@@ -74,6 +74,30 @@ def test_ivf_other_dims(hiplib, oracle, dim):
         _same(s[i], l[i], c[i], os_, ok, lambda k: labels[k])
 
 
+@pytest.mark.parametrize("metric", [0, 1])
+def test_ivf_build_with_a_nan_row(hiplib, oracle, metric):
+    """An all-NaN row through the whole Build (k-means training and the assignment): no centroid scores above
+    float.MinValue for it, so FindNearestCentroid leaves it with centroid 0 (KMeansUtils.cs:72-92), and cluster 0's
+    NaN mean compares equal to the old centroid (ArraysEqual, :57), which therefore stays.  Centroid bits and the
+    list layout equal the oracle's.  (The row's top-1 scan returns no key; that used to become list -1.)"""
+    from pyrope_amd import IvfFlatVectorIndex, generate_synthetic
+    n, d, nl = 3000, 64, 16
+    x = generate_synthetic(n, d, 34)
+    x[3] = np.nan
+    cents, assign = oracle.ivf_build(x, nl, metric)
+    assert assign[3] == 0 and not np.isnan(cents).any()
+    idx = IvfFlatVectorIndex(d, metric, n_list=nl)
+    idx.add_labels(np.arange(n, dtype=np.int64), x)
+    idx.build()
+    g = idx.centroids_array()
+    assert g.shape == cents.shape and np.array_equal(g.view(np.uint32), cents.view(np.uint32))
+    off, labels, live = idx.ivf_layout()
+    _, order, ooff = oracle.lists_from_assign(x, assign, len(cents))
+    np.testing.assert_array_equal(off, ooff)
+    np.testing.assert_array_equal(labels, order)
+    idx.close()
+
+
 def test_ivf_buffer_shadow_delete_and_max_scans(hiplib, oracle):
     """Rows added after Build live in the exact-scanned buffer; list rows with a buffered id are skipped
     (IvfFlatVectorIndex.cs:170-180, :210); Delete removes from both (:61-83); MaxScans counts both (:172,:202-212)."""
